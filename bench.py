@@ -7,10 +7,13 @@ trains), BERT-base, batch 256 per GPU, 70 text tokens + 5 phrase slots, 20 tag s
 of 2054-d features, all heads (masked-concept, contrastive, MLM, ITM, WRA), dropout 0.1 as in the
 reference config, bf16 MFMA kernels with f32 master weights.  Synthetic data, random-init weights.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
-Prints ONE JSON line on rank 0 (see DESIGN.md §Measurement for every field).
+Prints ONE JSON line on rank 0 (see DESIGN.md §Measurement for every field).  A plain run sets up, warms up, times the K
+steps and prints the headline; --full adds every other leg (all-slots-valid step, input pipeline, dominant-kernel replay,
+single-stream model, configs[3] / configs[4], CPU baseline, host enqueue time; at N > 1 the data-parallel legs).
+--dump-outputs DIR writes what the last timed step computed as DIR/<name>.npy (see dump_outputs).
 """
 import argparse
 import json
@@ -602,18 +605,48 @@ def _spawn_ranks(args):
     raise SystemExit("bench.py: no free rendezvous port after 3 attempts")
 
 
+DUMP_SAMPLE_PER_TENSOR = 16384
+
+
+def dump_outputs(out_dir, model, loss):
+    """What a caller of the timed step receives after its last call, as float32 .npy files in out_dir:
+      loss.npy            the loss that step returned, shape [1];
+      params_sample.npy   the f32 master weights that step left behind: every parameter in named_parameters() order, whole
+                          when it has at most DUMP_SAMPLE_PER_TENSOR elements, otherwise that many elements at flat indices
+                          drawn from a generator seeded 0 per tensor (the same positions in every run of the same model).
+    About 9 MB for the two-stage model."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, "loss.npy"), loss.detach().float().reshape(1).cpu().numpy())
+    parts = []
+    with torch.no_grad():
+        for _, p in model.named_parameters():
+            flat = p.detach().reshape(-1)
+            if flat.numel() > DUMP_SAMPLE_PER_TENSOR:
+                idx = torch.randint(0, flat.numel(), (DUMP_SAMPLE_PER_TENSOR,), generator=torch.Generator().manual_seed(0))
+                flat = flat[idx.to(flat.device)]
+            parts.append(flat.float().cpu())
+    np.save(os.path.join(out_dir, "params_sample.npy"), torch.cat(parts).numpy())
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--batch", type=int, default=256, help="pairs per GPU")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, every other leg: all-slots-valid step, input pipeline, dominant-kernel replay, "
+                         "single-stream model, configs[3] / configs[4], CPU baseline, host enqueue time; at N > 1 the data-parallel legs")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the loss and a fixed sample of the updated weights of the last timed step as DIR/<name>.npy")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--fixed-length", action="store_true", help="every token/region slot valid is the timed workload")
     ap.add_argument("--no-extras", action="store_true",
-                    help="timed steps only (no all-slots-valid leg, kernel replay or CPU baseline): the command profiles/ are made from")
+                    help="with --full: no all-slots-valid leg, kernel replay, single-stream, configs[3] / configs[4] or CPU baseline "
+                         "(the host enqueue time and the data-parallel legs stay); without --full it changes nothing")
     ap.add_argument("--with-input-pipeline", action="store_true",
-                    help="(default with the extras) extra leg: every step's batch comes from pinned host memory through "
+                    help="(on with --full) extra leg: every step's batch comes from pinned host memory through "
                          "input_pipeline.PretrainBatchStager (double-buffered H2D on a copy stream, bf16 K-padded features): the PCIe-inclusive rate")
     ap.add_argument("--max-grad-norm", type=float, default=10.0,
                     help="global-norm gradient clip inside the timed step (the reference's only working recipe clips at 10.0, "
@@ -643,6 +676,7 @@ def main():
     ap.add_argument("--threads", type=int, default=0, help=argparse.SUPPRESS)
     ap.add_argument("--budget", type=float, default=10.0, help=argparse.SUPPRESS)
     args = ap.parse_args()
+    extras = args.full and not args.no_extras     # the single-GPU legs beside the headline
 
     if args.cpu_baseline_child:   # CPU only: never touches the GPU
         fn = _cpu_baseline_bi if args.cpu_baseline_child == "bi" else _cpu_baseline_single
@@ -765,23 +799,27 @@ def main():
     n_text = int((lab_a > -1).sum().item())   # the heads run on the scored rows only
     n_tag = 0 if single else int((batch["lm_label_ids_b"] > -1).sum().item())
     ms_per_step, loss = timed(batch, args.warmup, args.steps)
+    if args.dump_outputs and rank == 0:      # before any other leg steps the model further
+        dump_outputs(args.dump_outputs, model, loss)
     # the host's share of a step, outside the timed region: three more steps, each queued behind an EMPTY queue (inside the timed
     # loop the host runs ahead until the launch queue is full and then waits for the GPU: its loop time says nothing)
-    host_enqueue_ms = []
-    for _ in range(3):
+    host_enqueue_ms = None
+    if args.full:
+        host_enqueue_ms = []
+        for _ in range(3):
+            torch.cuda.synchronize()
+            h0 = time.perf_counter()
+            step(batch)
+            host_enqueue_ms.append((time.perf_counter() - h0) * 1e3)
         torch.cuda.synchronize()
-        h0 = time.perf_counter()
-        step(batch)
-        host_enqueue_ms.append((time.perf_counter() - h0) * 1e3)
-    torch.cuda.synchronize()
-    host_enqueue_ms = sorted(host_enqueue_ms)[1]
+        host_enqueue_ms = sorted(host_enqueue_ms)[1]
     value = world * args.batch / (ms_per_step * 1e-3)
 
     # N > 1: what the ranks saw, what the exchange costs, and a second timed leg with the data-parallel opt-ins:
-    # the driver's plain `bench.py --gpus 8` then measures the conservative exchange (f32 wire, dense word-table exchange) AND
+    # `bench.py --gpus 8 --full` then measures the conservative exchange (f32 wire, dense word-table exchange) AND
     # bf16 wire + row-sparse word table (+ two streams where the headline ran one) in one run, same fences and step count.
     dp_info = None
-    if world > 1:
+    if world > 1 and args.full:
         import torch.distributed as dist
         ones = torch.ones(1, device=dev)
         dist.all_reduce(ones)
@@ -844,7 +882,7 @@ def main():
     # the encoder stacks run row-packed (the padded slots of the variable-length batch are not computed;
     # results agree with the padded execution to rounding).
     full = None
-    if not args.fixed_length and not args.no_extras:
+    if not args.fixed_length and extras:
         fb_batch = make_batch(True)
         full_ms, _ = timed(fb_batch, 2, args.steps)
         _, fb_full = flops_per_pair(dims, cfg, n_text / args.batch, n_tag / args.batch, single)
@@ -856,7 +894,7 @@ def main():
     # PCIe-inclusive rate (never `value`): the same batch staged from pinned host tensors every step, as a
     # DataLoader(pin_memory=True) would hand it over; the stager's copy stream overlaps the copy of batch i+1 with step i
     piped = None
-    if (args.with_input_pipeline or not args.no_extras) and not single and not args.fixed_length:
+    if (args.with_input_pipeline or extras) and not single and not args.fixed_length:
         from mvp_pytorch_amd.input_pipeline import PretrainBatchStager, INT_FIELDS
         host = {k: v.cpu().pin_memory() for k, v in batch.items() if k in INT_FIELDS or k == "img_feats"}
         stager = PretrainBatchStager(dev, args.batch, dims, cfg["img_feature_dim"], depth=2, features="both")
@@ -889,7 +927,7 @@ def main():
         else:
             _, fb_exec = flops_executed(batch, dims, cfg, n_text, n_tag, single)
         step_tflops = fb_exec / (ms_per_step * 1e-3) / 1e12
-        roof = {} if args.no_extras else kernel_roofline(dev, dims, cfg, None if args.fixed_length else batch, single)
+        roof = kernel_roofline(dev, dims, cfg, None if args.fixed_length else batch, single) if extras else {}
         roof["step_achieved"] = round(step_tflops, 1)
         roof["step_frac"] = round(step_tflops / MFMA_BF16_PEAK_TFLOPS, 4)
         roof["flops_per_step_executed"] = fb_exec
@@ -915,18 +953,18 @@ def main():
                        "all_slots_valid": full, "with_input_pipeline": piped, "max_grad_norm": args.max_grad_norm,
                        # wall time the host needs to queue one step's launches behind an empty queue (median of three steps
                        # after the timed region): the step is GPU-bound while this stays below ms_per_step
-                       "host_enqueue_ms_per_step": round(host_enqueue_ms, 2),
+                       "host_enqueue_ms_per_step": None if host_enqueue_ms is None else round(host_enqueue_ms, 2),
                        "hip_graph": {"enabled": bool(stepper.enabled), "captures": stepper.captures, "replayed_steps": stepper.replays,
                                      "eager_steps": stepper.eager_steps, "capture_error": stepper.last_error},
                        "data_parallel": dp_info},
             "roofline": roof,
         }
-        if world == 1 and not args.no_extras and not single:
+        if world == 1 and extras and not single:
             out["config"]["single_stream_model"] = _single_stream_line(args)
             del model, opt, sync, batch
             torch.cuda.empty_cache()
             out["config"]["secondary"] = _secondary_legs(dev, args.steps, args.no_graph)
-        if world == 1 and not args.no_cpu_baseline and not args.no_extras:
+        if world == 1 and extras and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(single=single)
         print(json.dumps(out), flush=True)
     if world > 1:

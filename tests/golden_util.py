@@ -90,10 +90,38 @@ def det_state_dict(shapes, seed, gain=1.0):
     return out
 
 
+PART_BYTES = 960 << 10     # a committed file stays below 1 MiB: larger fixtures go out as NAME.npz + NAME.partK.npz
+
+
+def _part_paths(name, out_dir=GOLDEN_DIR):
+    head = os.path.join(out_dir, name + ".npz")
+    parts = [f for f in os.listdir(out_dir) if f.startswith(name + ".part") and f.endswith(".npz")]
+    return [head] + [os.path.join(out_dir, f) for f in sorted(parts, key=lambda f: int(f[len(name) + 5:-4]))]
+
+
+def save(name, data, out_dir=GOLDEN_DIR):
+    """np.savez_compressed of one fixture, the arrays dealt (in their order) over NAME.npz, NAME.part2.npz, ... so that every
+    file stays below PART_BYTES; load() joins them."""
+    for p in _part_paths(name, out_dir)[1:]:
+        os.remove(p)
+    parts, cur, size = [], {}, 0
+    for k, v in data.items():
+        n = len(zlib.compress(np.asarray(v).tobytes(), 6)) + 512
+        if cur and size + n > PART_BYTES:
+            parts.append(cur)
+            cur, size = {}, 0
+        cur[k] = v
+        size += n
+    parts.append(cur)
+    for i, p in enumerate(parts):
+        np.savez_compressed(os.path.join(out_dir, name + (".npz" if i == 0 else ".part%d.npz" % (i + 1))), **p)
+
+
 def load(name):
-    path = os.path.join(GOLDEN_DIR, name + ".npz")
-    z = np.load(path, allow_pickle=False)
-    d = {k: z[k] for k in z.files}
+    d = {}
+    for path in _part_paths(name):
+        z = np.load(path, allow_pickle=False)
+        d.update({k: z[k] for k in z.files})
     d["config"] = json.loads(str(d["config_json"]))
     d["dims"] = json.loads(str(d["dims_json"]))
     return d

@@ -97,7 +97,7 @@ def test_bench_launcher_two_ranks_on_one_gpu(dev):
     for k in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT"):
         env.pop(k, None)
     o = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--batch", "16",
-                        "--no-extras"], env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=600)
+                        "--full", "--no-extras"], env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=600)
     assert o.returncode == 0, o.stderr.decode()[-2000:]
     line = json.loads(o.stdout.decode().strip().splitlines()[-1])
     assert line["n_gpus"] == 2 and line["steps"] == 2 and line["warmup"] == 1
@@ -117,6 +117,37 @@ def test_bench_launcher_two_ranks_on_one_gpu(dev):
     assert "error" not in zs, zs
     assert zs["ms_per_step"] > 0 and zs["steps"] == 2 and zs["optimizer_state_elements_per_rank"] > 0
     assert line["config"]["max_grad_norm"] == 10.0
+
+
+def test_bench_plain_run_is_lean_and_dumps_outputs(dev, tmp_path):
+    """A plain `bench.py --gpus 1` times exactly --steps steps, runs no leg beside the headline (those need --full) and with
+    --dump-outputs writes the loss and the weight sample of its last timed step."""
+    import json
+    import subprocess
+    import sys
+    import numpy as np
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = dict(os.environ)
+    for k in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT", "MVPTR_BENCH_DEVICE"):
+        env.pop(k, None)
+    out = tmp_path / "dump"
+    o = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--batch", "16",
+                        "--dump-outputs", str(out)], env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=600)
+    assert o.returncode == 0, o.stderr.decode()[-2000:]
+    line = json.loads(o.stdout.decode().strip().splitlines()[-1])
+    assert line["steps"] == 3 and line["warmup"] == 1 and line["ms_per_step"] > 0
+    assert abs(line["value"] - 16 / (line["ms_per_step"] * 1e-3)) < 0.02 * line["value"]
+    cfg = line["config"]
+    assert cfg["all_slots_valid"] is None and cfg["with_input_pipeline"] is None and cfg["host_enqueue_ms_per_step"] is None
+    assert cfg["data_parallel"] is None and "secondary" not in cfg and "single_stream_model" not in cfg and "cpu_baseline" not in line
+    assert "kernel" not in line["roofline"] and line["roofline"]["step_frac"] > 0
+    hg = cfg["hip_graph"]
+    if hg["captures"] == 1:       # 2 eager steps + the capture's own replay, then warm-up and timed steps: nothing else ran
+        assert hg["eager_steps"] == 2 and hg["replayed_steps"] == 1 + 1 + 3, hg
+    assert sorted(p.name for p in out.iterdir()) == ["loss.npy", "params_sample.npy"]
+    loss, params = np.load(out / "loss.npy"), np.load(out / "params_sample.npy")
+    assert loss.dtype == np.float32 and loss.shape == (1,) and abs(float(loss[0]) - cfg["final_loss"]) < 1e-3
+    assert params.dtype == np.float32 and 1e6 < params.size < (64 << 20) // 4 and np.isfinite(params).all()
 
 
 # ------------------------------------------------------------------------------ round-3: the RCCL path on one GPU

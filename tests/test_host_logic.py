@@ -445,6 +445,26 @@ def test_flops_formula_matches_survey():
     assert fb == 3 * fwd
 
 
+def test_bench_dump_outputs_layout():
+    """bench.py --dump-outputs: float32 loss + a sample of the weights at positions that are the same in every run."""
+    import bench
+    model = torch.nn.Sequential(torch.nn.Linear(300, 200), torch.nn.LayerNorm(200))
+    loss = torch.tensor(1.25)
+    with tempfile.TemporaryDirectory() as td:
+        bench.dump_outputs(td, model, loss)
+        l1, p1 = np.load(os.path.join(td, "loss.npy")), np.load(os.path.join(td, "params_sample.npy"))
+        bench.dump_outputs(td, model, loss)
+        p2 = np.load(os.path.join(td, "params_sample.npy"))
+        assert sorted(os.listdir(td)) == ["loss.npy", "params_sample.npy"]
+    n = bench.DUMP_SAMPLE_PER_TENSOR
+    assert l1.dtype == np.float32 and l1.tolist() == [1.25]
+    assert p1.dtype == np.float32 and p1.shape == (n + 200 + 200 + 200,) and np.array_equal(p1, p2)
+    w = model[0].weight.detach().reshape(-1)
+    idx = torch.randint(0, w.numel(), (n,), generator=torch.Generator().manual_seed(0))
+    assert np.array_equal(p1[:n], w[idx].numpy())                      # 60 000 elements: sampled
+    assert np.array_equal(p1[n:n + 200], model[0].bias.detach().numpy())   # small tensors: whole
+
+
 def test_weight_caches_are_per_device():
     """WeightCache / PackList hand out one object per device (nn.DataParallel replicas share the
     owning module's attributes by reference): first device -> the object itself, others -> children."""

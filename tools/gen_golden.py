@@ -226,7 +226,7 @@ def gen_bi_pretrain(name, c, dims, wseed, seed, full_grads, gain=1.0, lean=False
             data["adamw:" + n] = dict(model.named_parameters())[n].detach().numpy().copy()
     data["config_json"] = np.array(gu.to_json(c))
     data["dims_json"] = np.array(gu.to_json(dims))
-    np.savez_compressed(os.path.join(OUT, name + ".npz"), **data)
+    gu.save(name, data, OUT)
     print(name, "losses", data["losses"], "argmax margin", margin)
 
 
@@ -248,7 +248,7 @@ def gen_single_pretrain(name, c, dims, seed):
     data.update(grad_summary(model))
     data["config_json"] = np.array(gu.to_json(c))
     data["dims_json"] = np.array(gu.to_json(dims))
-    np.savez_compressed(os.path.join(OUT, name + ".npz"), **data)
+    gu.save(name, data, OUT)
     print(name, "losses", data["losses"])
 
 
@@ -303,7 +303,7 @@ def gen_finetune(name, c, dims, seed):
     data["config_json"] = np.array(gu.to_json(c))
     data["dims_json"] = np.array(gu.to_json(dims))
     data["seed"] = np.array(seed)
-    np.savez_compressed(os.path.join(OUT, name + ".npz"), **data)
+    gu.save(name, data, OUT)
     print(name, "ret", data["ret_train_losses"], "vqa", data["vqa_loss"], "ve", data["ve_loss"])
 
 
@@ -418,7 +418,7 @@ def gen_branches(name, c, dims, seed):
     data["config_json"] = np.array(gu.to_json(c))
     data["dims_json"] = np.array(gu.to_json(dims))
     data["seed"] = np.array(seed)
-    np.savez_compressed(os.path.join(OUT, name + ".npz"), **data)
+    gu.save(name, data, OUT)
     print(name, "qa losses", data["qa_losses"], "mlp", data["mlp_loss"], "soft", data["soft_loss"], "mse", data["mse_loss"],
           "bce", data["bce_loss"], "kl", data["kl_loss"])
 
@@ -465,7 +465,7 @@ def gen_features(name):
                 out["%s:%d:feat" % (tag, i)] = got.numpy()
             out[tag + ":D"] = np.array(D)
             out[tag + ":n"] = np.array(len(boxes))
-    np.savez_compressed(os.path.join(OUT, name + ".npz"), **out)
+    gu.save(name, out, OUT)
     print(name, "rows", sum(len(c[2]) for c in cases))
 
 

@@ -4,4 +4,4 @@ timeout 600 python3 -m pytest tests/test_ops_gpu.py -x -q -k "gemm_nt" > $O/pyte
 tail -15 $O/pytest_ops.txt
 MVPTR_LIB=diag timeout 600 python3 tools/blas_table.py --ab --ms 10917,37748,64000 > $O/blas_table_ab.txt 2>&1
 cat $O/blas_table_ab.txt
-timeout 600 python3 bench.py --steps 10 --warmup 3 --no-cpu-baseline > $O/bench.json 2> $O/bench.err; tail -3 $O/bench.err; cut -c1-400 $O/bench.json
+timeout 600 python3 bench.py --full --steps 10 --warmup 3 --no-cpu-baseline > $O/bench.json 2> $O/bench.err; tail -3 $O/bench.err; cut -c1-400 $O/bench.json

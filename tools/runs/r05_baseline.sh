@@ -3,7 +3,7 @@
 O=gpurun_out/r05a; mkdir -p $O
 cd $GRAFT_REPO_ROOT
 export TMPDIR=/tmp
-python3 bench.py > $O/bench_default.log 2>&1
+python3 bench.py --full > $O/bench_default.log 2>&1
 tail -1 $O/bench_default.log | cut -c1-600
 rocprofv3 --kernel-trace --output-format csv -d $O/blas -o blas -- python3 tools/blas_table.py --ms 37748,10917 --reps 2 > $O/blas_table.log 2>&1
 python3 - <<'PY' > gpurun_out/r05a/blas_kernels.txt 2>&1

@@ -35,5 +35,5 @@ python3 tools/gpu_idle.py $O/fixed/fixed_kernel_trace.csv > $O/r05_step_launches
 # keep only the summaries (the traces are tens of MB)
 find $O -name "*kernel_trace.csv" -size +2M -delete
 find $O -name "*counter_collection.csv" -size +8M -delete
-python3 bench.py > $O/r05_bench_default_line.txt 2> $O/bench_default.err
+python3 bench.py --full > $O/r05_bench_default_line.txt 2> $O/bench_default.err
 ls $O; tail -3 $O/bench_packed_under_rocprof.log | cut -c1-300; cat $O/roofline.log | head -70; cat $O/features.log

@@ -12,5 +12,5 @@ python3 tools/pmc_kernel.py $O/fetch_aligned FETCH_SIZE gemm_tn_sk_kernel
 python3 tools/pmc_kernel.py $O/fetch_flat FETCH_SIZE gemm_tn_sk_kernel
 find $O -name "*counter_collection.csv" -size +8M -delete
 unset MVPTR_LIB MVPTR_NT_EXP
-python3 bench.py --steps 30 --warmup 8 --no-extras 2>/dev/null | tail -1 | python3 -c "import json,sys; d=json.loads(sys.stdin.read()); print(d['ms_per_step'], d['config']['host_enqueue_ms_per_step'])"
-python3 bench.py --steps 30 --warmup 8 --no-extras --model single 2>/dev/null | tail -1 | python3 -c "import json,sys; d=json.loads(sys.stdin.read()); print(d['ms_per_step'], d['config']['host_enqueue_ms_per_step'])"
+python3 bench.py --full --steps 30 --warmup 8 --no-extras 2>/dev/null | tail -1 | python3 -c "import json,sys; d=json.loads(sys.stdin.read()); print(d['ms_per_step'], d['config']['host_enqueue_ms_per_step'])"
+python3 bench.py --full --steps 30 --warmup 8 --no-extras --model single 2>/dev/null | tail -1 | python3 -c "import json,sys; d=json.loads(sys.stdin.read()); print(d['ms_per_step'], d['config']['host_enqueue_ms_per_step'])"

@@ -9,7 +9,7 @@ done
 for r in 1 2; do
 for k in 0 262144 256; do
   echo "== bench packed, MVPTR_NT_EXP=$k" >> $O/ab.log
-  MVPTR_LIB=diag MVPTR_NT_EXP=$k python3 bench.py --steps 30 --warmup 8 --no-extras 2>/dev/null | python3 -c "import json,sys; d=json.loads(sys.stdin.readlines()[-1]); print(d['ms_per_step'], d['value'], d['config']['host_enqueue_ms_per_step'])" >> $O/ab.log 2>&1
+  MVPTR_LIB=diag MVPTR_NT_EXP=$k python3 bench.py --full --steps 30 --warmup 8 --no-extras 2>/dev/null | python3 -c "import json,sys; d=json.loads(sys.stdin.readlines()[-1]); print(d['ms_per_step'], d['value'], d['config']['host_enqueue_ms_per_step'])" >> $O/ab.log 2>&1
 done
 done
 cat $O/ab.log
