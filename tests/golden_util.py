@@ -143,3 +143,19 @@ class InjectHard:
 
     def __exit__(self, *exc):
         del self.bert.mine_hard_negatives
+
+
+def dropout_keep_np(n, seed_lo, seed_hi, thresh16):
+    """Independent numpy restatement of the dropout hash documented at mvptr_dropout (include/mvptr.h): one 32-bit hash
+    per element pair (2j, 2j+1), keep(i) = u16(i) >= thresh16 -> uint8 [n].  All arithmetic in uint64, wrapped to 32 bits."""
+    m32 = np.uint64(0xFFFFFFFF)
+    j = np.arange((n + 1) // 2, dtype=np.uint64)
+    x = (((j & m32) ^ np.uint64(seed_lo)) + (j >> np.uint64(32)) * np.uint64(0x9E3779B9)) & m32
+    x ^= x >> np.uint64(16)
+    x = (x * np.uint64(0x7FEB352D)) & m32
+    x ^= x >> np.uint64(15)
+    x = (x + np.uint64(seed_hi)) & m32
+    x = (x * np.uint64(0x846CA68B)) & m32
+    x ^= x >> np.uint64(16)
+    u16 = np.stack([x & np.uint64(0xFFFF), x >> np.uint64(16)], axis=1).reshape(-1)[:n]
+    return (u16 >= np.uint64(thresh16)).astype(np.uint8)
