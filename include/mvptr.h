@@ -483,7 +483,8 @@ int mvptr_tap_rows_bwd(const mvptr_tap* taps, int ntaps, void* dst, int64_t ld_d
  * Replaces the masked_select chains of oscar/modeling/modeling_vlbert.py:1231-1234,1245. */
 enum { MVPTR_DEV_ERR_SCORED_ROWS = 1,   /* mvptr_compact_scored: more scored slots than output slots */
        MVPTR_DEV_ERR_PHRASES = 2,       /* host-side check queued by the model: a sample has more phrases than config.max_phrases */
-       MVPTR_DEV_ERR_FEW_REGIONS = 3 }; /* config.wra_strict: an image with phrases has fewer than 3 regions (topk(3), vl:1547) */
+       MVPTR_DEV_ERR_FEW_REGIONS = 3,   /* config.wra_strict: an image with phrases has fewer than 3 regions (topk(3), vl:1547) */
+       MVPTR_DEV_ERR_ROW_BOUND = 4 };   /* mvptr_check_bounds: more valid rows (or a longer sequence) than the bounded pass was sized for */
 int mvptr_compact_scored(const int64_t* labels, const int32_t* pos, int64_t ld_pos, int B, int L, int n_out,
                          int64_t* out_labels, int32_t* out_rows, int64_t* err, void* stream);
 
@@ -509,6 +510,14 @@ typedef struct {
 } mvptr_pack_seg;
 int mvptr_pack_maps(const mvptr_pack_seg* segs, int nseg, int n_seq, int32_t* pos_out, int32_t* idx_out,
                     int32_t* seq_start, int32_t* seq_len, int64_t* counts, void* stream);
+/* The same maps for a pass whose buffers hold row_limit (> 0) rows, fewer than there are slots (a BOUNDED pass: the buffers are
+ * sized for a bound on the valid rows, the count stays on the device).  idx_out int32 [row_limit]: the entries between the count
+ * and row_limit are written -1 (zero rows of mvptr_gather_rows).  seq_start / seq_len are clamped to [0, row_limit], a valid
+ * slot whose packed row would be >= row_limit reads -1 in pos_out and gets no idx_out entry, and a slot whose own source map
+ * (pos) holds -1 yields idx_out = -1: whatever the masks hold, nothing built from these maps addresses a row >= row_limit.
+ * counts[] keep the TRUE totals (mvptr_check_bounds reports an overrun).  Additive in ABI 7. */
+int mvptr_pack_maps_bounded(const mvptr_pack_seg* segs, int nseg, int n_seq, int row_limit, int32_t* pos_out, int32_t* idx_out,
+                            int32_t* seq_start, int32_t* seq_len, int64_t* counts, void* stream);
 
 /* Host-provided counts against the device's: counts_a / counts_b are the `counts` outputs of two mvptr_pack_maps calls (int64 [2]:
  * rows, longest); a value that differs from the host's number traps the kernel (the process aborts with a message).  This is the
@@ -517,6 +526,12 @@ int mvptr_pack_maps(const mvptr_pack_seg* segs, int nseg, int n_seq, int32_t* po
  * error check on the host with one read-back instead: BiBertImgModel.verify_host_counts.) */
 int mvptr_check_counts(const int64_t* counts_a, const int64_t* counts_b, int64_t rows_a, int64_t lmax_a, int64_t rows_b, int64_t lmax_b,
                        void* stream);
+/* The same counts against BOUNDS (a bounded pass: rows <= bound_rows_*, longest sequence <= *_width).  Neither traps nor prints:
+ * the kernels of a bounded pass work on min(device count, bound) rows, so carrying on is memory-safe (rows past the bound drop
+ * out).  An overrun is written to the device error word `err` (see mvptr_compact_scored; must not be NULL): err[0] =
+ * MVPTR_DEV_ERR_ROW_BOUND if no error is pending (first error wins), err[1] = the count found, err[2] = its bound.  Additive in ABI 7. */
+int mvptr_check_bounds(const int64_t* counts_a, const int64_t* counts_b, int64_t bound_rows_a, int64_t la_width, int64_t bound_rows_b,
+                       int64_t lb_width, int64_t* err, void* stream);
 
 /* Word-region alignment loss (phrase_mod == 'sample'), replaces oscar/modeling/modeling_vlbert.py:1285-1300 with
  * get_pos_neg_sims :1553-1596 and t2i_sim :1543-1550 on rows already gathered from the joint output:

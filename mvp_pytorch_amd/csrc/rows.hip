@@ -40,7 +40,10 @@ __global__ __launch_bounds__(256) void pack_count_kernel(mvptr_pack_seg s0, mvpt
   if (lane == 0) seq_len[s] = cnt;
 }
 
-__global__ __launch_bounds__(1024) void pack_scan_kernel(const int32_t* seq_len, int n_seq, int32_t* seq_start, int64_t* counts) {
+// row_limit: rows of the buffers behind the maps (a bounded pass; INT_MAX: every slot has a row).  seq_start / seq_len leave
+// clamped to it, so that no kernel that walks a sequence (attention) can step past the buffers whatever the masks hold;
+// counts[] keep the TRUE totals (mvptr_check_bounds reports an overrun, the layer kernels take min(count, bound)).
+__global__ __launch_bounds__(1024) void pack_scan_kernel(int32_t* seq_len, int n_seq, int row_limit, int32_t* seq_start, int64_t* counts) {
   __shared__ int scan[1024];
   __shared__ int carry_s, maxlen_s;
   const int tid = threadIdx.x;
@@ -62,7 +65,9 @@ __global__ __launch_bounds__(1024) void pack_scan_kernel(const int32_t* seq_len,
     }
     const int carry = carry_s;
     if (s < n_seq) {
-      seq_start[s] = carry + scan[tid] - cnt;
+      const int st = min(carry + scan[tid] - cnt, row_limit);
+      seq_start[s] = st;
+      if (cnt > row_limit - st) seq_len[s] = row_limit - st;
       atomicMax(&maxlen_s, cnt);
     }
     __syncthreads();
@@ -75,10 +80,17 @@ __global__ __launch_bounds__(1024) void pack_scan_kernel(const int32_t* seq_len,
   }
 }
 
-__global__ __launch_bounds__(256) void pack_fill_kernel(mvptr_pack_seg s0, mvptr_pack_seg s1, int nseg, int n_seq,
-                                                         const int32_t* seq_start, int32_t* pos_out, int32_t* idx_out) {
+__global__ __launch_bounds__(256) void pack_fill_kernel(mvptr_pack_seg s0, mvptr_pack_seg s1, int nseg, int n_seq, int row_limit,
+                                                         const int32_t* seq_start, int32_t* pos_out, int32_t* idx_out,
+                                                         const int64_t* tail_from) {
   const int lane = threadIdx.x & 63;
   const int s = blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (tail_from != nullptr) {
+    // bounded pass: the entries between the count and the bound read -1 (zero rows of the gather) — written here instead of by a
+    // fill launch in front of the maps
+    const int64_t t0 = min(tail_from[0], (int64_t)row_limit);
+    for (int64_t j = t0 + blockIdx.x * 256 + threadIdx.x; j < row_limit; j += (int64_t)gridDim.x * 256) idx_out[j] = -1;
+  }
   if (s >= n_seq) return;
   const int Ltot = s0.len + (nseg > 1 ? s1.len : 0);
   int32_t* po = pos_out + (int64_t)s * Ltot;
@@ -95,12 +107,13 @@ __global__ __launch_bounds__(256) void pack_fill_kernel(mvptr_pack_seg s0, mvptr
       const bool ok = in && (m[l] == 0.f);
       const uint64_t bal = __ballot(ok);
       const int dest = run + __popcll(bal & lt);
-      if (in) po[slot0 + l] = ok ? dest : -1;
-      if (ok) {
+      const bool fits = ok && dest < row_limit;      // a valid slot past the bound has no row: it reads as padding
+      if (in) po[slot0 + l] = fits ? dest : -1;
+      if (fits) {
         const int64_t src = g.pos ? (int64_t)g.pos[r * g.ld_pos + g.col0 + l] : r * g.src_seq_stride + g.col0 + l;
-        idx_out[dest] = (int32_t)(src + g.src_base);
+        idx_out[dest] = src >= 0 ? (int32_t)(src + g.src_base) : -1;      // (a slot its own map left without a row: zero row)
       }
-      run += __popcll(bal);
+      run = min(run + __popcll(bal), row_limit);
     }
     slot0 += g.len;
   }
@@ -262,8 +275,9 @@ __global__ __launch_bounds__(256) void tap_sum_kernel(TapSet ts, int R, int spli
 
 }  // namespace
 
-extern "C" int mvptr_pack_maps(const mvptr_pack_seg* segs, int nseg, int n_seq, int32_t* pos_out, int32_t* idx_out,
-                               int32_t* seq_start, int32_t* seq_len, int64_t* counts, void* stream) {
+namespace {
+int pack_maps_impl(const mvptr_pack_seg* segs, int nseg, int n_seq, int row_limit, bool fill_tail, int32_t* pos_out,
+                   int32_t* idx_out, int32_t* seq_start, int32_t* seq_len, int64_t* counts, void* stream) {
   if (!segs || nseg < 1 || nseg > 2 || n_seq <= 0) MVPTR_FAIL(MVPTR_BAD_ARG, "pack_maps: 1 or 2 segments, n_seq > 0");
   if (!pos_out || !idx_out || !seq_start || !seq_len || !counts) MVPTR_FAIL(MVPTR_BAD_ARG, "pack_maps: NULL output");
   for (int k = 0; k < nseg; ++k)
@@ -271,10 +285,23 @@ extern "C" int mvptr_pack_maps(const mvptr_pack_seg* segs, int nseg, int n_seq, 
   mvptr_pack_seg s1 = segs[nseg > 1 ? 1 : 0];
   const dim3 grid((n_seq + 3) / 4);
   hipLaunchKernelGGL(pack_count_kernel, grid, dim3(256), 0, (hipStream_t)stream, segs[0], s1, nseg, n_seq, seq_len);
-  hipLaunchKernelGGL(pack_scan_kernel, dim3(1), dim3(1024), 0, (hipStream_t)stream, seq_len, n_seq, seq_start, counts);
-  hipLaunchKernelGGL(pack_fill_kernel, grid, dim3(256), 0, (hipStream_t)stream, segs[0], s1, nseg, n_seq, seq_start, pos_out, idx_out);
+  hipLaunchKernelGGL(pack_scan_kernel, dim3(1), dim3(1024), 0, (hipStream_t)stream, seq_len, n_seq, row_limit, seq_start, counts);
+  hipLaunchKernelGGL(pack_fill_kernel, grid, dim3(256), 0, (hipStream_t)stream, segs[0], s1, nseg, n_seq, row_limit, seq_start, pos_out,
+                     idx_out, fill_tail ? counts : nullptr);
   MVPTR_CHECK_LAUNCH("pack_maps");
   return MVPTR_OK;
+}
+}  // namespace
+
+extern "C" int mvptr_pack_maps_bounded(const mvptr_pack_seg* segs, int nseg, int n_seq, int row_limit, int32_t* pos_out,
+                                       int32_t* idx_out, int32_t* seq_start, int32_t* seq_len, int64_t* counts, void* stream) {
+  if (row_limit <= 0) MVPTR_FAIL(MVPTR_BAD_ARG, "pack_maps_bounded: row_limit must be positive");
+  return pack_maps_impl(segs, nseg, n_seq, row_limit, true, pos_out, idx_out, seq_start, seq_len, counts, stream);
+}
+
+extern "C" int mvptr_pack_maps(const mvptr_pack_seg* segs, int nseg, int n_seq, int32_t* pos_out, int32_t* idx_out,
+                               int32_t* seq_start, int32_t* seq_len, int64_t* counts, void* stream) {
+  return pack_maps_impl(segs, nseg, n_seq, 0x7fffffff, false, pos_out, idx_out, seq_start, seq_len, counts, stream);
 }
 
 extern "C" int mvptr_gather_rows(const void* src, int64_t ld_src, const void* src2, int64_t ld_src2, int split,
@@ -483,5 +510,35 @@ extern "C" int mvptr_check_counts(const int64_t* counts_a, const int64_t* counts
   if (!counts_a || !counts_b) MVPTR_FAIL(MVPTR_BAD_ARG, "check_counts: NULL argument");
   hipLaunchKernelGGL(check_counts_kernel, dim3(1), dim3(1), 0, (hipStream_t)stream, counts_a, counts_b, rows_a, lmax_a, rows_b, lmax_b);
   MVPTR_CHECK_LAUNCH("check_counts");
+  return MVPTR_OK;
+}
+
+// Device counts against the BOUNDS a bounded pass was sized for (train.GraphedStep(bucket=...): one captured graph serves every
+// batch whose counts fit its buffers).  Unlike mvptr_check_counts this one neither traps nor prints: every kernel behind it works
+// on min(device count, bound) rows (rows_clamped, the clamped maps of mvptr_pack_maps_bounded), so carrying on is memory-safe;
+// the overrun goes into the device error word (first error wins; err[1] = found, err[2] = the bound) and the host raises later.
+namespace {
+__global__ void check_bounds_kernel(const int64_t* a, const int64_t* b, int64_t ra, int64_t la, int64_t rb, int64_t lb,
+                                    unsigned long long* err) {
+  int64_t found = 0, bound = 0;
+  if (a[0] > ra) { found = a[0]; bound = ra; }
+  else if (a[1] > la) { found = a[1]; bound = la; }
+  else if (b[0] > rb) { found = b[0]; bound = rb; }
+  else if (b[1] > lb) { found = b[1]; bound = lb; }
+  else return;
+  if (atomicCAS(err, 0ull, (unsigned long long)MVPTR_DEV_ERR_ROW_BOUND) == 0ull) {
+    err[1] = (unsigned long long)found;
+    err[2] = (unsigned long long)bound;
+  }
+}
+}  // namespace
+
+extern "C" int mvptr_check_bounds(const int64_t* counts_a, const int64_t* counts_b, int64_t bound_rows_a, int64_t la_width,
+                                  int64_t bound_rows_b, int64_t lb_width, int64_t* err, void* stream) {
+  if (!counts_a || !counts_b || !err) MVPTR_FAIL(MVPTR_BAD_ARG, "check_bounds: NULL argument");
+  if (bound_rows_a <= 0 || la_width <= 0 || bound_rows_b <= 0 || lb_width <= 0) MVPTR_FAIL(MVPTR_BAD_ARG, "check_bounds: bounds must be positive");
+  hipLaunchKernelGGL(check_bounds_kernel, dim3(1), dim3(1), 0, (hipStream_t)stream, counts_a, counts_b, bound_rows_a, la_width,
+                     bound_rows_b, lb_width, reinterpret_cast<unsigned long long*>(err));
+  MVPTR_CHECK_LAUNCH("check_bounds");
   return MVPTR_OK;
 }

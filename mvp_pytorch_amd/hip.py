@@ -37,6 +37,7 @@ SYMBOLS = [
     "mvptr_hard_negative_mine", "mvptr_bce_logits", "mvptr_check_counts", "mvptr_tap_rows_bwd",
     "mvptr_masked_mean", "mvptr_dgelu_mul", "mvptr_compact_scored",
     "mvptr_gemm_tn_stack", "mvptr_encoder_layer_bwd_defer", "mvptr_set_dropout_salt",
+    "mvptr_check_bounds", "mvptr_pack_maps_bounded",
 ]
 # include/mvptr_diag.h: exported by the diagnostic build only (MVPTR_LIB=diag)
 DIAG_SYMBOLS = ["mvptr_diag_stream_read", "mvptr_diag_store_probe", "mvptr_diag_fill_probe", "mvptr_set_knob"]
@@ -145,6 +146,7 @@ def load():
     lib.mvptr_hard_negative_mine.argtypes = [P, I, I64, P, P, P, P, P, P, P, P]
     lib.mvptr_bce_logits.argtypes = [P, P, I, I, P, P, P, I, P]
     lib.mvptr_check_counts.argtypes = [P, P, I64, I64, I64, I64, P]
+    lib.mvptr_check_bounds.argtypes = [P, P, I64, I64, I64, I64, P, P]
     lib.mvptr_masked_mean.argtypes = [P, P, I, P, P]
     lib.mvptr_compact_scored.argtypes = [P, P, I64, I, I, I, P, P, P, P]
     lib.mvptr_dgelu_mul.argtypes = [P, I64, P, I64, I, P, I64, I, I, I, P]
@@ -156,6 +158,7 @@ def load():
     lib.mvptr_gather_rows.argtypes = [P, I64, P, I64, I, P, P, I64, I, I, P]
     lib.mvptr_scatter_add_rows.argtypes = [P, I64, I, P, P, I64, P, I64, I, I, I, I, P]
     lib.mvptr_pack_maps.argtypes = [POINTER(PackSeg), I, I, P, P, P, P, P, P]
+    lib.mvptr_pack_maps_bounded.argtypes = [POINTER(PackSeg), I, I, I, P, P, P, P, P, P]
     lib.mvptr_wra_rows.argtypes = [P, I, P, P, I, I, I, P, P, P]
     lib.mvptr_wra_fwd.argtypes = [P, P, P, P, P, P, P, I, I, I, I, P, P, P, P, P, P, P, P, P]
     lib.mvptr_wra_bwd.argtypes = [P, P, P, I, I, I, I, P, P, P, P, P, P, P, P, P, P]
@@ -723,11 +726,13 @@ def scatter_add_rows(src, idx, dst, dst2=None):
 # ROCm both abort the whole process.  Now such a check writes a code into a small per-device int64 word; the host looks at it
 # whenever it reads ANYTHING back from that device (engine.AsyncCounts carries word[0] along with every count copy;
 # check_device_errors() reads it explicitly) and raises RuntimeError there, one step late at most, with the process intact.
-DEV_ERR_SCORED_ROWS, DEV_ERR_PHRASES, DEV_ERR_FEW_REGIONS = 1, 2, 3
+DEV_ERR_SCORED_ROWS, DEV_ERR_PHRASES, DEV_ERR_FEW_REGIONS, DEV_ERR_ROW_BOUND = 1, 2, 3, 4
 DEV_ERR_TEXT = {
     DEV_ERR_SCORED_ROWS: "more scored (label > -1) slots than the host's count: host_counts.scored_* does not describe this batch",
     DEV_ERR_PHRASES: "a sample has more phrases than config.max_phrases",
     DEV_ERR_FEW_REGIONS: "word-region alignment needs >= 3 valid regions per image (topk(3), modeling_vlbert.py:1547)",
+    DEV_ERR_ROW_BOUND: "more valid rows (or a longer sequence) than the bound this pass was sized for: host_counts.bound_rows_* "
+                       "does not cover this batch (the rows past the bound dropped out of the step)",
 }
 _err_words = {}
 
@@ -766,6 +771,8 @@ def raise_device_error(code, device=None):
             vals = [int(v) for v in w.tolist()]
             if code == DEV_ERR_SCORED_ROWS:
                 detail = " (%d scored rows, %d slots)" % (vals[1], vals[2])
+            elif code == DEV_ERR_ROW_BOUND:
+                detail = " (found %d, bound %d)" % (vals[1], vals[2])
             w.zero_()
     raise RuntimeError("device-side check failed: " + DEV_ERR_TEXT.get(code, "error code %d" % code) + detail)
 
@@ -850,10 +857,12 @@ def tap_rows_bwd(taps, rows, rows2, H):
     return d, d2
 
 
-def pack_maps(segs, n_seq, fill_idx=False):
+def pack_maps(segs, n_seq, fill_idx=False, row_limit=None):
     """segs: 1 or 2 dicts(mask f32 [rows, ld] additive, sel int64 [n_seq] or None, col0, len, pos int32 [rows, ld_pos] or
     None, src_seq_stride, src_base) -> (pos int32 [n_seq, Ltot], idx int32 [n_seq * Ltot] (first `rows` entries valid),
-    seq_start int32 [n_seq], seq_len int32 [n_seq], counts int64 [2] = rows, longest) — see mvptr_pack_maps."""
+    seq_start int32 [n_seq], seq_len int32 [n_seq], counts int64 [2] = rows, longest) — see mvptr_pack_maps.
+    row_limit: the maps of a BOUNDED pass (mvptr_pack_maps_bounded): idx has row_limit entries (-1 past the count) and no
+    map names a row >= row_limit whatever the masks hold; counts keep the true totals."""
     dev = segs[0]["mask"].device
     arr = (PackSeg * len(segs))()
     Ltot = 0
@@ -871,11 +880,20 @@ def pack_maps(segs, n_seq, fill_idx=False):
     pos_out = torch.empty((n_seq, Ltot), device=dev, dtype=torch.int32)
     # fill_idx: entries past the valid rows read -1 (a gather of the WHOLE vector then yields zero rows there: the
     # sync-free joint pass, whose row count stays on the device)
-    idx_out = (torch.full if fill_idx else torch.empty)(*(((n_seq * Ltot,), -1) if fill_idx else ((n_seq * Ltot,),)), device=dev, dtype=torch.int32)
+    if row_limit is not None:
+        row_limit = int(row_limit)
+        assert 0 < row_limit <= n_seq * Ltot
+    n_idx = n_seq * Ltot if row_limit is None else row_limit
+    fill_idx = fill_idx and row_limit is None       # the bounded maps write the -1 tail themselves
+    idx_out = (torch.full if fill_idx else torch.empty)(*(((n_idx,), -1) if fill_idx else ((n_idx,),)), device=dev, dtype=torch.int32)
     seq_start = torch.empty(n_seq, device=dev, dtype=torch.int32)
     seq_len = torch.empty(n_seq, device=dev, dtype=torch.int32)
     counts = torch.empty(2, device=dev, dtype=torch.int64)
-    _check(load().mvptr_pack_maps(arr, len(segs), n_seq, _p(pos_out), _p(idx_out), _p(seq_start), _p(seq_len), _p(counts), _stream()))
+    if row_limit is None:
+        _check(load().mvptr_pack_maps(arr, len(segs), n_seq, _p(pos_out), _p(idx_out), _p(seq_start), _p(seq_len), _p(counts), _stream()))
+    else:
+        _check(load().mvptr_pack_maps_bounded(arr, len(segs), n_seq, row_limit, _p(pos_out), _p(idx_out), _p(seq_start), _p(seq_len),
+                                              _p(counts), _stream()))
     return pos_out, idx_out, seq_start, seq_len, counts
 
 
@@ -883,6 +901,14 @@ def check_counts(counts_a, counts_b, expect):
     """mvptr_check_counts: the device-side counts of two pack_maps calls (int64 [2] each: rows, longest) must equal the
     host's numbers `expect` = (rows_a, lmax_a, rows_b, lmax_b); a mismatch traps the kernel (the process aborts)."""
     _check(load().mvptr_check_counts(_p(counts_a), _p(counts_b), int(expect[0]), int(expect[1]), int(expect[2]), int(expect[3]), _stream()))
+
+
+def check_bounds(counts_a, counts_b, bounds):
+    """mvptr_check_bounds: the device-side counts of two pack_maps calls against `bounds` = (bound_rows_a, La, bound_rows_b, Lb)
+    of a bounded pass.  An overrun goes into the device error word (DEV_ERR_ROW_BOUND; raised by check_device_errors / the next
+    read-back / train.GraphedStep's next call) — the kernel neither traps nor prints, the step behind it stays inside its buffers."""
+    _check(load().mvptr_check_bounds(_p(counts_a), _p(counts_b), int(bounds[0]), int(bounds[1]), int(bounds[2]), int(bounds[3]),
+                                     _p(device_error_word(counts_a.device)), _stream()))
 
 
 def wra_rows(pos, phrase_index, img_index, n, Pw, Rw):

@@ -94,6 +94,9 @@ def additive_mask(attention_mask):
 # dies with its module and is never copied or pickled with it
 import weakref as _weakref
 _JOINT_PENDING = _weakref.WeakKeyDictionary()
+# Keys a bounded step adds to host_counts (the one place that names them; train.bucket_bounds writes them): the uni-modal passes
+# and the scored-row slots of the two MLM heads are sized for these instead of the exact counts beside them
+BOUND_KEYS = ("bound_rows_a", "bound_rows_b", "bound_scored_a", "bound_scored_b")
 
 class CaptionBertLayer(BertLayer):
     pass
@@ -651,7 +654,15 @@ class BiBertImgModel(_ImgBackboneMixin, BertPreTrainedModel):
         that only needs those (queued on the side stream beside the joint stack).
         -> dict: both (packed joint output [rows_j, H]; sequences 0..n-1 matched, n..2n-1 hard), pos_j int32 [2n, Lj]
         (packed row of every slot of the unpadded joint layout, -1 = padded), seq_start_j, sim_mat, hard_txt_full,
-        hard_img_full, pos_a, pos_b, n_txt_rows."""
+        hard_img_full, pos_a, pos_b, n_txt_rows.
+
+        host_counts may also carry BOUNDS (BOUND_KEYS: bound_rows_a, bound_rows_b; bound_scored_* are read by the task model):
+        the two uni-modal passes then run like the joint pass — buffers of bound_rows_* rows, the row count on the device
+        (rows_dev = the count of hip.pack_maps, rows_plan = the host's exact count), attention tiles for the padded widths La /
+        Lb, the second source of the joint map and of the taps at offset bound_rows_a.  No launch argument but the planning hint
+        depends on the exact counts, so every batch that fits the bounds can replay one captured graph
+        (train.GraphedStep(bucket=...)).  Counts above a bound are reported through the device error word
+        (mvptr_check_bounds: RuntimeError at the host's next look, the rows past the bound drop out; nothing traps)."""
         from .. import hip
         dev = input_ids_a.device
         B, La = input_ids_a.shape
@@ -662,8 +673,16 @@ class BiBertImgModel(_ImgBackboneMixin, BertPreTrainedModel):
         if token_type_ids_b is None:
             token_type_ids_b = torch.zeros_like(input_ids_b)
         mask_a, mask_b = additive_mask(attention_mask_a), additive_mask(attention_mask_b)
-        pos_a, idx_a, st_a, ln_a, cnt_a = hip.pack_maps([dict(mask=mask_a, len=La, src_seq_stride=La)], B)
-        pos_b, idx_b, st_b, ln_b, cnt_b = hip.pack_maps([dict(mask=mask_b, len=Lb, src_seq_stride=Lb)], B)
+        bounded = host_counts is not None and BOUND_KEYS[0] in host_counts
+        if bounded:
+            if getattr(self, "verify_host_counts", False):
+                raise ValueError("verify_host_counts reads the counts back: not available with bounds in host_counts")
+            Ra = min(max(int(host_counts[BOUND_KEYS[0]]), 1), B * La)
+            Rb = min(max(int(host_counts[BOUND_KEYS[1]]), 1), B * Lb)
+        else:
+            Ra = Rb = None
+        pos_a, idx_a, st_a, ln_a, cnt_a = hip.pack_maps([dict(mask=mask_a, len=La, src_seq_stride=La)], B, row_limit=Ra)
+        pos_b, idx_b, st_b, ln_b, cnt_b = hip.pack_maps([dict(mask=mask_b, len=Lb, src_seq_stride=Lb)], B, row_limit=Rb)
         # rows / longest sequence of the two uni-modal passes: from the caller (host_counts, computed where the batch was
         # built) or read back from the device behind the embedding kernels
         counts = None if host_counts is not None else engine.AsyncCounts([cnt_a[0], cnt_a[1], cnt_b[0], cnt_b[1]])
@@ -684,7 +703,9 @@ class BiBertImgModel(_ImgBackboneMixin, BertPreTrainedModel):
             main.wait_stream(side)
         if host_counts is not None:
             ra, la_max, rb, lb_max = (int(host_counts[k]) for k in ("rows_a", "lmax_a", "rows_b", "lmax_b"))
-            if getattr(self, "verify_host_counts", False):
+            if bounded:
+                hip.check_bounds(cnt_a, cnt_b, (Ra, La, Rb, Lb))      # device-side: counts <= bounds (error word, no trap)
+            elif getattr(self, "verify_host_counts", False):
                 # bring-up mode of a data pipeline: one read-back, a catchable error instead of the device-side trap
                 got = [int(v) for v in torch.cat([cnt_a, cnt_b]).tolist()]
                 if got != [ra, la_max, rb, lb_max]:
@@ -693,21 +714,32 @@ class BiBertImgModel(_ImgBackboneMixin, BertPreTrainedModel):
                 hip.check_counts(cnt_a, cnt_b, (ra, la_max, rb, lb_max))      # device-side: host_counts must describe this batch's masks
         else:
             ra, la_max, rb, lb_max = counts.get()
-        xa_p = engine.tap_rows(xa.view(B * La, H), idx_a[:ra])
+        if bounded:
+            # idx_* hold bound_rows_* entries, -1 past the count: the gathers yield zero rows there and every layer kernel clamps to
+            # the device-side count (workgroups past it return at once); the attention tiles are those of the padded widths
+            ia, ib = idx_a, idx_b
+            kw_a = dict(rows_dev=cnt_a, rows_plan=min(ra, Ra))
+            kw_b = dict(rows_dev=cnt_b, rows_plan=min(rb, Rb))
+            la_max, lb_max = La, Lb
+            ra = Ra                                    # offset of the second source (a host constant of the bounds)
+        else:
+            ia, ib = idx_a[:ra], idx_b[:rb]
+            kw_a = kw_b = {}
+        xa_p = engine.tap_rows(xa.view(B * La, H), ia)
         if two_streams:
             side.wait_stream(main)
             with torch.cuda.stream(side):
-                xb_p = engine.tap_rows(xb.view(B * Lb, H), idx_b[:rb])
-                vis_p = self.vis_encoder.forward_rows(xb_p, st_b, ln_b, B, lb_max)
-            txt_p = self.txt_encoder.forward_rows(xa_p, st_a, ln_a, B, la_max)
+                xb_p = engine.tap_rows(xb.view(B * Lb, H), ib)
+                vis_p = self.vis_encoder.forward_rows(xb_p, st_b, ln_b, B, lb_max, **kw_b)
+            txt_p = self.txt_encoder.forward_rows(xa_p, st_a, ln_a, B, la_max, **kw_a)
             main.wait_stream(side)
             for t in (xb, idx_b, st_b, ln_b):
                 t.record_stream(side)
             vis_p.record_stream(main)
         else:
-            xb_p = engine.tap_rows(xb.view(B * Lb, H), idx_b[:rb])
-            txt_p = self.txt_encoder.forward_rows(xa_p, st_a, ln_a, B, la_max)
-            vis_p = self.vis_encoder.forward_rows(xb_p, st_b, ln_b, B, lb_max)
+            xb_p = engine.tap_rows(xb.view(B * Lb, H), ib)
+            txt_p = self.txt_encoder.forward_rows(xa_p, st_a, ln_a, B, la_max, **kw_a)
+            vis_p = self.vis_encoder.forward_rows(xb_p, st_b, ln_b, B, lb_max, **kw_b)
         # [CLS] states + whatever else the caller reads from the uni-modal outputs: one tap call
         extra_t, extra_v = uni_taps(pos_a, pos_b) if uni_taps is not None else ([], [])
         cls_t, cls_v = pos_a[:, 0].contiguous(), pos_b[:, 0].contiguous()
@@ -1159,7 +1191,12 @@ class BiBertImgForPreTraining(ImgPreTrainedModel):
         n, La = input_ids_a.shape
         from .. import hip
         if host_counts is not None:
-            n_scored = (int(host_counts["scored_a"]), int(host_counts["scored_b"]))
+            # bounds (BOUND_KEYS) take the place of the exact counts: mvptr_compact_scored pads the surplus slots with label -1 / row
+            # -1, the heads ignore them and the mean divides by the device-side number of scored rows (mvptr_masked_mean)
+            if BOUND_KEYS[2] in host_counts:
+                n_scored = (max(int(host_counts[BOUND_KEYS[2]]), 1), max(int(host_counts[BOUND_KEYS[3]]), 1))
+            else:
+                n_scored = (int(host_counts["scored_a"]), int(host_counts["scored_b"]))
         else:
             scored = engine.AsyncCounts([(masked_lm_labels_a > -1).sum(), (masked_lm_labels_b > -1).sum()])
             n_scored = None

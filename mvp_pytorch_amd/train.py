@@ -126,6 +126,59 @@ def pretrain_step(model, batch, optimizer, scheduler, max_tag_length=20, loss_we
     return loss.detach()
 
 
+# ---- bounds of a bucketed step (GraphedStep(bucket=...)) --------------------------------------------------------------------
+# Order of the four numbers everywhere below: valid rows of the text / of the tag + region input, scored rows of the two MLM heads
+COUNT_KEYS = ("rows_a", "rows_b", "scored_a", "scored_b")
+BUCKET_DEFAULT = dict(rows=1024, scored=256)
+
+
+def bucket_quanta(bucket):
+    """GraphedStep's `bucket` argument -> (rows quantum, scored quantum)"""
+    q = dict(BUCKET_DEFAULT) if bucket is True else dict(BUCKET_DEFAULT, **dict(bucket))
+    if set(q) != set(BUCKET_DEFAULT) or min(int(v) for v in q.values()) < 1:
+        raise ValueError("bucket: True or dict(rows=<quantum >= 1>, scored=<quantum >= 1>), got %r" % (bucket,))
+    return int(q["rows"]), int(q["scored"])
+
+
+def batch_caps(batch):
+    """the most a count can be: every slot of the padded batch (B*La, B*Lb, B*La, B*Lb)"""
+    na, nb = batch["input_mask_a"].numel(), batch["input_mask_b"].numel()
+    return (na, nb, na, nb)
+
+
+def bucket_bounds(counts, caps, quanta):
+    """counts rounded UP to their quantum (at least one quantum: a buffer of no rows is not a buffer), capped at caps"""
+    q = (quanta[0], quanta[0], quanta[1], quanta[1])
+    return tuple(min(max(-(-int(c) // k), 1) * k, int(cap)) for c, k, cap in zip(counts, q, caps))
+
+
+def covers(bounds, counts):
+    return all(int(b) >= int(c) for b, c in zip(bounds, counts))
+
+
+def cover_bounds(known, counts, caps, quanta, rank=None):
+    """The covering rule: the tightest of the bounds in `known` that cover `counts` (smallest sum; rank(bounds), when given, goes
+    first — the stepper prefers a bound whose graph exists already), else new bounds — plain rounding, raised to cover every set
+    in `known` too — appended to `known`.
+    Plain rounding alone gives a batch just above a quantum boundary and one just below it two signatures; here the second one
+    rides in the first one's buffers.  -> (bounds, created)"""
+    fit = [b for b in known if covers(b, counts)]
+    if fit:
+        return min(fit, key=lambda b: ((rank(b) if rank is not None else 0), sum(b), b)), False
+    b = bucket_bounds(counts, caps, quanta)
+    for k in known:                 # new bounds also cover every older set: the bounds form a chain and its last member serves all
+        b = tuple(max(x, y) for x, y in zip(b, k))
+    known.append(b)
+    return b, True
+
+
+def same_input(prev, v):
+    """Replay copy-skip rule: `prev` = (tensor, _version) noted at the last copy into a graph's buffer.  Only THE SAME TENSOR OBJECT
+    at the same version skips the copy (a loop over one batch).  An address match says nothing: a fresh `.to(device)` batch has
+    version 0 and commonly lands where the freed previous batch was (the step then trained on the previous batch)."""
+    return prev is not None and prev[0] is v and prev[1] == v._version
+
+
 class GraphedStep:
     """pretrain_step whose DEVICE work is captured once per batch signature as a HIP graph and replayed (the host
     needs 7-9 ms to queue the ~460 launches of a step; a replay is one launch).  Same contract as pretrain_step: every call is one
@@ -145,11 +198,26 @@ class GraphedStep:
     A signature (tensor shapes + dtypes + the host counts + train mode) is stepped eagerly `warm_steps` times first (allocations,
     weight copies, optimizer state), then captured; a capture that fails — a host read-back (batches without host_counts), a
     collective, an unfused optimizer group — is remembered and that signature stays eager.  Variable-length data gives every
-    batch its own counts, i.e. its own signature: such jobs run eagerly (bound-sized uni-modal passes would lift that; not built).
+    batch its own counts, i.e. its own signature: with bucket=None (the default) such jobs run eagerly once max_graphs are taken.
+
+    bucket=dict(rows=<quantum>, scored=<quantum>) or True (1024 / 256): ONE graph for many variable-length batches.  The two
+    uni-modal passes and the scored-row slots are sized for BOUNDS — the batch's counts rounded up to the quantum, capped at
+    B*La / B*Lb — and the counts stay on the device (modeling_vlbert.BOUND_KEYS in host_counts; BiBertImgModel.forward_packed).
+    The signature is then tensor shapes + dtypes + train mode + the bounds; a batch replays the tightest captured graph whose
+    bounds cover its counts, and new bounds are made (warmed up through the same bounded path, then captured) only when none
+    does (cover_bounds).  A batch whose host_counts already carry bounds keeps them.  `signatures` counts the bounded
+    signatures seen.  Scope: the two-stage pre-training model (BiBertImgForPreTraining, with or without phrase_index); the
+    single-stream model, the fine-tune wrappers and a custom `forward` keep exact signatures whatever `bucket` says.
+
+    In both modes: a replay copies every input into the graph's buffers unless it is the same tensor object at the same version
+    as at the last copy (same_input); and after every replay the device error word is copied to pinned memory — the copy of an
+    earlier replay that has landed is looked at when the next call starts (no wait) and a failed device-side check (too few
+    scored-row slots, counts above the bounds: rows dropped from the step, nothing out of bounds) raises RuntimeError there.
+    check() waits for the copies still in flight (end of an epoch).
     Multi-rank jobs run eagerly (the bucketed exchange is driven from Python hooks)."""
 
     def __init__(self, model, optimizer, scheduler, max_tag_length=20, loss_weight=1.0, max_grad_norm=0.0, grad_sync=None,
-                 warm_steps=2, max_graphs=4, enabled=True, forward=None):
+                 warm_steps=2, max_graphs=4, enabled=True, forward=None, bucket=None):
         self.forward = forward       # callable(model, batch) -> outputs, loss first (default: the pre-training batch layout, model_inputs)
         self.model, self.optimizer, self.scheduler = model, optimizer, scheduler
         self.max_tag_length, self.loss_weight, self.max_grad_norm, self.grad_sync = max_tag_length, loss_weight, max_grad_norm, grad_sync
@@ -157,6 +225,10 @@ class GraphedStep:
         self._seen = {}        # signature -> eager steps so far
         self._graphs = {}      # signature -> dict(graph, static, plan, loss, outputs) | None (capture failed: stay eager)
         self.replays = self.eager_steps = self.captures = 0
+        self.quanta = None if bucket is None or bucket is False else bucket_quanta(bucket)
+        self._known = {}       # bucket mode: shapes part of the signature -> the bounds made so far, oldest first
+        self._err_pending = [] # (pinned int64 [1], event) of the replays whose error-word copy has not been looked at
+        self._err_device = None
         self.last_error = None
         self._stream = None
 
@@ -166,7 +238,41 @@ class GraphedStep:
         return pretrain_step(self.model, batch, self.optimizer, self.scheduler, self.max_tag_length, self.loss_weight,
                              self.max_grad_norm, self.grad_sync, return_losses, self.forward)
 
-    def _signature(self, batch):
+    @property
+    def signatures(self):
+        """distinct bounded signatures seen (bucket mode)"""
+        return sum(len(v) for v in self._known.values())
+
+    def _bucketed(self, batch):
+        """bucket mode applies: the two-stage pre-training batch with its host counts, through the model's own forward"""
+        if self.quanta is None or self.forward is not None:
+            return False
+        from .modeling.modeling_vlbert import BiBertImgForPreTraining
+        hc = batch.get("host_counts")
+        return (isinstance(self.model, BiBertImgForPreTraining) and isinstance(hc, dict) and "input_mask_a" in batch and
+                "input_mask_b" in batch and all(k in hc for k in COUNT_KEYS))
+
+    def _bound(self, batch):
+        """-> (batch with the bounds in its host_counts, its signature): the covering rule over this shape's bounds so far"""
+        from .modeling.modeling_vlbert import BOUND_KEYS
+        hc = batch["host_counts"]
+        base = self._signature(batch, with_counts=False)
+        if base is None:
+            return batch, None
+        known = self._known.setdefault(base, [])
+        if all(k in hc for k in BOUND_KEYS):                       # the caller's own bounds
+            bounds = tuple(int(hc[k]) for k in BOUND_KEYS)
+            if bounds not in known:
+                known.append(bounds)
+        else:
+            counts = tuple(int(hc[k]) for k in COUNT_KEYS)
+            captured = lambda b: 0 if self._graphs.get(base + (("bounds", b),)) else 1      # noqa: E731
+            bounds, _ = cover_bounds(known, counts, batch_caps(batch), self.quanta, rank=captured)
+        out = dict(batch)
+        out["host_counts"] = type(hc)(hc, **dict(zip(BOUND_KEYS, bounds)))
+        return out, base + (("bounds", bounds),)
+
+    def _signature(self, batch, with_counts=True):
         items = []
         for k in sorted(batch):
             v = batch[k]
@@ -175,6 +281,8 @@ class GraphedStep:
                     return None
                 items.append((k, tuple(v.shape), str(v.dtype)))
             elif isinstance(v, dict):
+                if not with_counts:
+                    continue            # bucket mode: the bounds stand in for the exact counts
                 items.append((k, tuple(sorted((kk, int(vv)) for kk, vv in v.items()))))
             elif getattr(v, "host_only", False):
                 continue                # host-side companions of a batch (synthetic.HostRows): not an input of the device work
@@ -192,8 +300,29 @@ class GraphedStep:
         p = next(self.model.parameters(), None)
         return p is not None and p.is_cuda and hasattr(self.optimizer, "advance")
 
+    def _look_at_errors(self, wait=False):
+        """the error-word copies of earlier replays: those that have landed (all of them with wait=True), oldest first"""
+        from . import hip
+        while self._err_pending and (wait or len(self._err_pending) > 8 or self._err_pending[0][1].query()):
+            word, ev = self._err_pending.pop(0)
+            ev.synchronize()            # (returns at once unless waiting was asked for, or the host is > 8 replays ahead)
+            if int(word[0]) != 0:
+                del self._err_pending[:]        # raise_device_error clears the word: later copies of the same error are stale
+                torch.cuda.synchronize(self._err_device)
+                hip.raise_device_error(int(word[0]), self._err_device)
+
+    def check(self):
+        """wait for the replays queued so far and raise RuntimeError if a device-side check of one of them failed"""
+        self._look_at_errors(wait=True)
+
     def __call__(self, batch, return_losses=False):
-        sig = self._signature(batch) if self._capturable() else None
+        self._look_at_errors()
+        sig = None
+        if self._capturable():
+            if self._bucketed(batch):
+                batch, sig = self._bound(batch)
+            else:
+                sig = self._signature(batch)
         if sig is None:
             return self._eager(batch, return_losses)
         # Every step of a capturable job — eager warm-up, capture, replay — runs on this object's own stream: autograd pins an
@@ -275,15 +404,25 @@ class GraphedStep:
         return ent
 
     def _replay(self, ent, batch, return_losses):
+        from . import hip
         static, last = ent["static"], ent.setdefault("last", {})
         for k, v in batch.items():
             if isinstance(v, torch.Tensor):
-                tag = (v.data_ptr(), v._version)
-                if last.get(k) != tag:                     # the same tensor, unchanged since its last copy (a loop over one batch): no copy
+                if not same_input(last.get(k), v):         # the same tensor object, unchanged since its last copy (a loop over one batch): no copy
                     static[k].copy_(v, non_blocking=True)
-                    last[k] = tag
+                    last[k] = (v, v._version)
         self.optimizer.advance(ent["plan"])
         ent["graph"].replay()
+        # the device error word of this replay, for the start of a later call (nothing waits here)
+        dev = next(self.model.parameters()).device
+        word = hip.device_error_word(dev)
+        if word is not None:
+            pinned = torch.empty(1, dtype=torch.int64, pin_memory=True)
+            pinned.copy_(word[:1], non_blocking=True)
+            ev = torch.cuda.Event()
+            ev.record()
+            self._err_device = dev
+            self._err_pending.append((pinned, ev))
         self.scheduler.step()
         self.replays += 1
         if return_losses:
