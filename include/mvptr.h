@@ -386,7 +386,8 @@ int mvptr_clip_coef(const float* partials, int n, float max_norm, float* norm_ou
  * `txt_out[:,0] @ txt_proj` (:525-526), the similarity matrix `global_txt @ global_img.t()` (:527) and the
  * gradients of all four.  op(X) = X or X^T (trans_x); A / B are f32 or bf16 (x_bf16) with unit column
  * stride; a_rows / b_rows (optional, int32) gather A's / B's STORED rows — the [CLS] rows of a padded or
- * row-packed sequence buffer are read in place; act: 0 none, 1 tanh; accumulate != 0: C += (a gradient arena). */
+ * row-packed sequence buffer are read in place; act: 0 none, 1 tanh, 2 ReLU (max(v, 0): the MLP heads of
+ * oscar/modeling/modeling_vlbert.py:1990-1994,2003-2007; additive in ABI 7); accumulate != 0: C += (a gradient arena). */
 int mvptr_sgemm_small(const void* A, int64_t lda, int a_bf16, int trans_a, const int32_t* a_rows, const void* B,
                       int64_t ldb, int b_bf16, int trans_b, const int32_t* b_rows, int M, int N, int K, float alpha,
                       const float* bias, int act, int accumulate, float* C, int64_t ldc, void* stream);
@@ -435,6 +436,27 @@ int mvptr_hard_negative_mine(const float* sim, int n, int64_t ld, const int64_t*
  * parts: f32 [n_parts] scratch (one partial sum per workgroup, added in index order: reproducible). */
 int mvptr_bce_logits(const float* logits, const float* labels, int rows, int cols, float* loss, float* dlogits,
                      float* parts, int n_parts, void* stream);
+
+/* ---- feature fusion of the BiImageBertForSequenceClassificationPlus head (fusion.hip; additive in ABI 7) ------
+ * The two concat-and-dropout stages of oscar/modeling/modeling_vlbert.py:2040-2043 in one launch each.  All operands f32 with
+ * unit column stride, row strides (lda, ldb, ldo, ...) in elements, rows >= 1, P >= 1 columns per input row:
+ *   MVPTR_FUSE_CAT2   out[r, :] = dropout([a_r, b_r]),                        W = 2 P   (torch.cat([pooled_output, single_hidden], 1)
+ *                     + nn.Dropout, vl:2043)
+ *   MVPTR_FUSE_PAIR4  out[r, :] = dropout([a_r, b_r, b_r - a_r, b_r * a_r]),  W = 4 P   (a = global_txt, b = global_img, vl:2040-2041)
+ * drop: NULL = no dropout; the dropout element index of out[r, c] is r * W + c (the row stride ldo does not enter; rows * W < 2^33).
+ * Backward, with g_s = keep * scale * dout on segment s (dout f32 [rows, W], row stride ldd; the same descriptor as forward):
+ *   CAT2: da = g_0, db = g_1;   PAIR4: da = g_0 - g_2 + g_3 * b, db = g_1 + g_2 + g_3 * a.    da / db are written, not accumulated.
+ * 16-byte loads and stores when P % 4 == 0, every row stride is a multiple of 4 and every base is 16-byte aligned; any other
+ * layout takes an element-wise path with the same results. */
+#define MVPTR_FUSE_CAT2 0
+#define MVPTR_FUSE_PAIR4 1
+int mvptr_fuse_features_fwd(const float* a, int64_t lda, const float* b, int64_t ldb, int rows, int P, int mode,
+                            const mvptr_dropout* drop, float* out, int64_t ldo, void* stream);
+int mvptr_fuse_features_bwd(const float* a, int64_t lda, const float* b, int64_t ldb, const float* dout, int64_t ldd, int rows, int P,
+                            int mode, const mvptr_dropout* drop, float* da, int64_t ldda, float* db, int64_t lddb, void* stream);
+/* du[i] = y[i] > 0 ? dy[i] : 0 over n contiguous f32 elements: the backward of the act = 2 epilogue of mvptr_sgemm_small from its
+ * saved OUTPUT y. */
+int mvptr_relu_bwd(const float* dy, const float* y, float* du, int64_t n, void* stream);
 
 /* ---- rows between the stacks (rows.hip) ------------------------------------------------------------------
  * Row gather / scatter-add over bf16 [rows, H] buffers: out[i,:] = src[idx[i],:] (idx < 0: zero row) and

@@ -21,7 +21,7 @@ struct SgemmArgs {
   int M, N, K;
   int trans_a, trans_b;   // 0: as stored [M,K] / [K,N]; 1: stored transposed ([K,M] / [N,K])
   int a_bf16, b_bf16;     // element type of A / B (0: f32, 1: bf16)
-  int act;                // 0: none, 1: tanh
+  int act;                // 0: none, 1: tanh, 2: ReLU
   int accumulate;         // C += result (gradients into an arena) instead of C =
   float alpha;
 };
@@ -136,6 +136,7 @@ __global__ __launch_bounds__(256) void sgemm_small_kernel(SgemmArgs p) {
     if (mr >= p.M) continue;
     float v = ((acc[r] + red[0][r][lane]) + (red[1][r][lane] + red[2][r][lane])) * p.alpha + bias;
     if (p.act == 1) v = tanhf(v);
+    else if (p.act == 2) v = v < 0.f ? 0.f : v;
     float* c = p.C + (int64_t)mr * p.ldc + n;
     *c = p.accumulate ? (*c + v) : v;
   }
@@ -268,7 +269,7 @@ extern "C" int mvptr_sgemm_small(const void* A, int64_t lda, int a_bf16, int tra
                                  int act, int accumulate, float* C, int64_t ldc, void* stream) {
   if (M <= 0 || N <= 0 || K <= 0) MVPTR_FAIL(MVPTR_BAD_SHAPE, "sgemm_small: M, N, K must be > 0");
   if (!A || !B || !C) MVPTR_FAIL(MVPTR_BAD_ARG, "sgemm_small: NULL argument");
-  if (act < 0 || act > 1) MVPTR_FAIL(MVPTR_BAD_ARG, "sgemm_small: unknown activation %d", act);
+  if (act < 0 || act > 2) MVPTR_FAIL(MVPTR_BAD_ARG, "sgemm_small: unknown activation %d", act);
   SgemmArgs p;
   p.A = A; p.B = B; p.C = C; p.bias = bias; p.a_rows = a_rows; p.b_rows = b_rows;
   p.lda = lda; p.ldb = ldb; p.ldc = ldc;

@@ -13,6 +13,7 @@ Functions
   LayerNormFn    BertLayerNorm on bf16 rows                     modeling_bert.py:242-246
   DecoderCEFn    vocabulary decoder + CrossEntropyLoss          modeling_bert.py:513-516,
                                                                 modeling_vlbert.py:1228-1249
+  FuseFeaturesFn concat-and-dropout stages of the Plus head     modeling_vlbert.py:2040-2043
 """
 import ctypes
 import os
@@ -1185,15 +1186,17 @@ def tap_rows(src, idx, src2=None):
 
 class SmallLinearFn(GradAwareFunction):
     """y = act(x W^T + b) in f32 on a few hundred rows: x bf16 or f32 [n, K], W f32 [N, K] (w_kn=False, nn.Linear
-    layout) or [K, N] (w_kn=True: `x @ W`, the CLIP projections vl:525-526), act in {None, 'tanh'} -> f32 [n, N].
-    Pooler (modeling_bert.py:468-474), seq_relationship (vl:975-979), txt_proj / vis_proj."""
+    layout) or [K, N] (w_kn=True: `x @ W`, the CLIP projections vl:525-526), act in {None, 'tanh', 'relu'} -> f32 [n, N].
+    Pooler (modeling_bert.py:468-474), seq_relationship (vl:975-979), txt_proj / vis_proj, the ReLU layers of the
+    BiImageBertForSequenceClassificationPlus head (vl:1990-1994,2003-2007)."""
 
     @staticmethod
     def forward(ctx, x, weight, bias, act, w_kn):
         x = x.contiguous()
         w = _f32(weight)
         y = hip.sgemm_small(x, w, trans_b=not w_kn, bias=_f32(bias) if bias is not None else None, act=act)
-        ctx.save = (x, w, y if act == "tanh" else None)
+        ctx.save = (x, w, y if act in ("tanh", "relu") else None)
+        ctx.act = act
         ctx.ps = (weight, bias)
         ctx.w_kn = w_kn
         ctx.needs = (x.requires_grad, weight.requires_grad, bias is not None and bias.requires_grad)
@@ -1205,7 +1208,9 @@ class SmallLinearFn(GradAwareFunction):
         x, w, y = ctx.save
         weight, bias = ctx.ps
         du = dy.contiguous().float()
-        if y is not None:
+        if ctx.act == "relu":
+            du = hip.relu_bwd(du, y)
+        elif y is not None:
             du = du * (1.0 - y * y)
         dx = dw = db = None
         dw_d = db_d = False
@@ -1223,6 +1228,29 @@ class SmallLinearFn(GradAwareFunction):
         ctx.save = ctx.ps = None
         return (dx, grad_result(weight, dw, dw_d) if ctx.needs[1] else None,
                 grad_result(bias, db, db_d) if ctx.needs[2] else None, None, None)
+
+
+class FuseFeaturesFn(torch.autograd.Function):
+    """The concat-and-dropout stages of the BiImageBertForSequenceClassificationPlus head in one launch each way:
+    mode hip.FUSE_CAT2 dropout(cat([a, b], 1)) (vl:2043), hip.FUSE_PAIR4 dropout(cat([a, b, b - a, b * a], 1)) (vl:2040-2041);
+    a, b f32 [rows, P].  p > 0 and training: one next_seed() per call; the mask is recomputed in backward from the descriptor."""
+
+    @staticmethod
+    def forward(ctx, a, b, mode, p, training):
+        a = a if a.stride(-1) == 1 else a.contiguous()
+        b = b if b.stride(-1) == 1 else b.contiguous()
+        drop = hip.make_dropout(p, next_seed()) if (p > 0 and training) else None
+        ctx.save = (a, b, drop)
+        ctx.mode = mode
+        return hip.fuse_features_fwd(a, b, mode, drop)
+
+    @staticmethod
+    def backward(ctx, dout):
+        a, b, drop = ctx.save
+        ctx.save = None
+        dout = dout.float()
+        da, db = hip.fuse_features_bwd(a, b, dout if dout.stride(-1) == 1 else dout.contiguous(), ctx.mode, drop)
+        return da, db, None, None, None
 
 
 class L2NormFn(torch.autograd.Function):

@@ -38,6 +38,7 @@ SYMBOLS = [
     "mvptr_masked_mean", "mvptr_dgelu_mul", "mvptr_compact_scored",
     "mvptr_gemm_tn_stack", "mvptr_encoder_layer_bwd_defer", "mvptr_set_dropout_salt",
     "mvptr_check_bounds", "mvptr_pack_maps_bounded",
+    "mvptr_fuse_features_fwd", "mvptr_fuse_features_bwd", "mvptr_relu_bwd",
 ]
 # include/mvptr_diag.h: exported by the diagnostic build only (MVPTR_LIB=diag)
 DIAG_SYMBOLS = ["mvptr_diag_stream_read", "mvptr_diag_store_probe", "mvptr_diag_fill_probe", "mvptr_set_knob"]
@@ -143,6 +144,10 @@ def load():
     lib.mvptr_clip_coef.argtypes = [P, I, F, P, P, P]
     lib.mvptr_sgemm_small.argtypes = [P, I64, I, I, P, P, I64, I, I, P, I, I, I, F, P, I, I, P, I64, P]
     lib.mvptr_ce_mean_small.argtypes = [P, I64, P, I, I, P, P, P]
+    if hasattr(lib, "mvptr_fuse_features_fwd"):      # (absent from older builds loaded for A/B runs through MVPTR_LIB)
+        lib.mvptr_fuse_features_fwd.argtypes = [P, I64, P, I64, I, I, I, POINTER(Dropout), P, I64, P]
+        lib.mvptr_fuse_features_bwd.argtypes = [P, I64, P, I64, P, I64, I, I, I, POINTER(Dropout), P, I64, P, I64, P]
+        lib.mvptr_relu_bwd.argtypes = [P, P, P, I64, P]
     lib.mvptr_hard_negative_mine.argtypes = [P, I, I64, P, P, P, P, P, P, P, P]
     lib.mvptr_bce_logits.argtypes = [P, P, I, I, P, P, P, I, P]
     lib.mvptr_check_counts.argtypes = [P, P, I64, I64, I64, I64, P]
@@ -610,6 +615,9 @@ def grad_clip_coef(flats, max_norm, scratch=None):
     return norm, coef, scratch
 
 
+SGEMM_ACT = {None: 0, "tanh": 1, "relu": 2}      # mvptr_sgemm_small `act`
+
+
 def sgemm_small(a, b, trans_a=False, trans_b=False, a_rows=None, b_rows=None, bias=None, act=None, alpha=1.0, out=None,
                 accumulate=False, m=None, n=None, k=None):
     """C = act(alpha * op(A) op(B) + bias) in f32 (mvptr_sgemm_small).  a / b: 2-D f32 or bf16 tensors with unit
@@ -625,8 +633,48 @@ def sgemm_small(a, b, trans_a=False, trans_b=False, a_rows=None, b_rows=None, bi
         out = torch.empty((M_, N_), device=a.device, dtype=torch.float32)
     _check(load().mvptr_sgemm_small(_p(a), a.stride(0), int(a.dtype == torch.bfloat16), int(trans_a), _p(a_rows), _p(b), b.stride(0),
                                     int(b.dtype == torch.bfloat16), int(trans_b), _p(b_rows), M_, N_, K_, float(alpha), _p(bias),
-                                    1 if act == "tanh" else 0, int(accumulate), _p(out), out.stride(0), _stream()))
+                                    SGEMM_ACT[act], int(accumulate), _p(out), out.stride(0), _stream()))
     return out
+
+
+FUSE_CAT2, FUSE_PAIR4 = 0, 1      # MVPTR_FUSE_*
+
+
+def _fuse_rows(t, name):
+    if t.dtype != torch.float32 or t.dim() != 2 or t.stride(1) != 1:
+        raise TypeError("fuse_features: %s must be a 2-D f32 tensor with unit column stride" % name)
+    return t
+
+
+def fuse_features_fwd(a, b, mode, drop=None):
+    """mvptr_fuse_features_fwd: a, b f32 [rows, P] (row-strided views allowed) -> dropout([a, b]) (FUSE_CAT2, [rows, 2P]) or
+    dropout([a, b, b - a, b * a]) (FUSE_PAIR4, [rows, 4P]); dropout element index of out[r, c] = r * W + c."""
+    _fuse_rows(a, "a"), _fuse_rows(b, "b")
+    assert a.shape == b.shape
+    rows, P = a.shape
+    out = torch.empty((rows, (4 if mode == FUSE_PAIR4 else 2) * P), device=a.device, dtype=torch.float32)
+    _check(load().mvptr_fuse_features_fwd(_p(a), a.stride(0), _p(b), b.stride(0), rows, P, int(mode), _dp(drop), _p(out), out.stride(0),
+                                          _stream()))
+    return out
+
+
+def fuse_features_bwd(a, b, dout, mode, drop=None):
+    """Backward of fuse_features_fwd with the same descriptor: dout f32 [rows, W] -> (da, db) f32 [rows, P], written."""
+    _fuse_rows(a, "a"), _fuse_rows(b, "b"), _fuse_rows(dout, "dout")
+    rows, P = a.shape
+    assert a.shape == b.shape and tuple(dout.shape) == (rows, (4 if mode == FUSE_PAIR4 else 2) * P)
+    da, db = torch.empty((rows, P), device=a.device, dtype=torch.float32), torch.empty((rows, P), device=a.device, dtype=torch.float32)
+    _check(load().mvptr_fuse_features_bwd(_p(a), a.stride(0), _p(b), b.stride(0), _p(dout), dout.stride(0), rows, P, int(mode), _dp(drop),
+                                          _p(da), da.stride(0), _p(db), db.stride(0), _stream()))
+    return da, db
+
+
+def relu_bwd(dy, y):
+    """mvptr_relu_bwd: du = dy where y > 0, else 0 (contiguous f32, y = the saved output of an act="relu" product)."""
+    assert dy.dtype == torch.float32 and y.dtype == torch.float32 and dy.is_contiguous() and y.is_contiguous() and dy.shape == y.shape
+    du = torch.empty_like(dy)
+    _check(load().mvptr_relu_bwd(_p(dy), _p(y), _p(du), dy.numel(), _stream()))
+    return du
 
 
 def l2norm_fwd(y, eps=1e-12):

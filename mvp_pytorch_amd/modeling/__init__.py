@@ -6,7 +6,8 @@ from .modeling_utils import ImgPreTrainedModel, PreTrainedModel, PretrainedConfi
 from . import modeling_vlbert
 from .modeling_vlbert import (BertImgForPreTraining, BertImgModel, BiBertImgForPreTraining,  # noqa: F401
                               BiBertImgModel, BiImageBertForRetrieval,
-                              BiImageBertForSequenceClassification, BiImageBertForVQA)
+                              BiImageBertForSequenceClassification, BiImageBertForSequenceClassificationPlus,
+                              BiImageBertForVQA)
 
 
 def make_config(cfg_dict, **overrides):

@@ -6,6 +6,7 @@ oscar/modeling/modeling_vlbert.py, running on the HIP encoder.
   BertImgForPreTraining        vl:1024-1130    BiBertImgForPreTraining    vl:1133-1311
   BiImageBertForRetrieval      vl:1598-1712    BiImageBertForSequenceClassification vl:1715-1798
   BiImageBertForVQA            vl:1801-1870    WRA helpers                vl:1502-1596
+  BiImageBertForSequenceClassificationPlus     vl:1975-2070
 
 (`vl` = oscar/modeling/modeling_vlbert.py in the reference tree.)  Keyword arguments, return
 tuples, state_dict keys and config attributes follow the reference; encoder activations are
@@ -510,12 +511,20 @@ class BiBertImgModel(_ImgBackboneMixin, BertPreTrainedModel):
             return engine.tap_rows(seq.view(B * L, H), engine.arange(B, seq.device, torch.int32, step=L))
         return seq[:, 0, :]
 
-    def _project(self, cls_rows, proj):
-        """normalize(cls @ proj) in f32 (vl:525-526; feeds the hard-negative argmax: kept out of bf16)."""
+    def _project(self, cls_rows, proj, raw_out=None):
+        """normalize(cls @ proj) in f32 (vl:525-526; feeds the hard-negative argmax: kept out of bf16).  raw_out (a list): the
+        un-normalised product is appended — BiImageBertForSequenceClassificationPlus feeds it to its head (vl:2037-2038), the
+        product is formed once."""
         if cls_rows.is_cuda and proj.dtype == torch.float32:
-            return engine.L2NormFn.apply(engine.SmallLinearFn.apply(cls_rows, proj, None, None, True))
+            raw = engine.SmallLinearFn.apply(cls_rows, proj, None, None, True)
+            if raw_out is not None:
+                raw_out.append(raw)
+            return engine.L2NormFn.apply(raw)
         # documented torch paths only (INTEGRATION.md §1): fp16 parameters of model.half() inference, CPU tensors
-        return F.normalize(cls_rows.float() @ proj.float(), p=2, dim=-1)
+        raw = cls_rows.float() @ proj.float()
+        if raw_out is not None:
+            raw_out.append(raw)
+        return F.normalize(raw, p=2, dim=-1)
 
     @staticmethod
     def _sim(global_txt, global_img):
@@ -524,15 +533,17 @@ class BiBertImgModel(_ImgBackboneMixin, BertPreTrainedModel):
             return engine.SimFn.apply(global_txt, global_img)
         return global_txt @ global_img.t()
 
-    def _globals(self, txt, vis):
-        return self._project(self._cls_rows(txt), self.txt_proj), self._project(self._cls_rows(vis), self.vis_proj)
+    def _globals(self, txt, vis, raw_out=None):
+        return (self._project(self._cls_rows(txt), self.txt_proj, raw_out),
+                self._project(self._cls_rows(vis), self.vis_proj, raw_out))
 
     def forward(self, input_ids_a, token_type_ids_a=None, attention_mask_a=None, max_tag_length=None,
                 use_b=False, position_ids_a=None, input_ids_b=None, token_type_ids_b=None,
                 attention_mask_b=None, phrase_layer=None, position_ids_b=None, head_mask=None,
                 img_feats=None, encoder_history_states=None, encode_hn=False, hn_mod="hard", logit=None,
-                pack_hints=None, beside=None, host_counts=None):
-        """host_counts (optional, encode_hn=False paths; synthetic.finetune_host_counts): rows / longest sequence of the three
+                pack_hints=None, beside=None, host_counts=None, raw_globals=None):
+        """raw_globals (optional list, not a reference argument): receives the un-normalised (global_txt, global_img) of vl:525-526.
+        host_counts (optional, encode_hn=False paths; synthetic.finetune_host_counts): rows / longest sequence of the three
         row-packed passes computed where the batch was built — no read-back inside the step (checked on the device against the
         masks, mvptr_check_counts: a mismatch traps, every buffer behind it is sized from these numbers).
         beside: optional callable(txt, vis, sim_mat) with work that only needs the uni-modal outputs (the visual
@@ -559,7 +570,7 @@ class BiBertImgModel(_ImgBackboneMixin, BertPreTrainedModel):
         cut = 1 if use_b else max_tag_length
         only_vis = vis[:, cut:, :]
         only_vis_mask = mask_b[:, cut:]
-        global_txt, global_img = self._globals(txt, vis)
+        global_txt, global_img = self._globals(txt, vis, raw_globals)
         sim_mat = self._sim(global_txt, global_img)
 
         hard_out = hard_pooled = hard_txt_full = hard_img_full = None
@@ -1631,6 +1642,96 @@ class BiImageBertForVQA(_FreezeMixin, BertPreTrainedModel):
                                   attention_mask_b=attention_mask_b, max_tag_length=max_tag_length, encode_hn=False,
                                   host_counts=host_counts)
         logits = self.cls(self.dropout(outputs[0][:, 0]))
+        out = (logits,) + outputs[2:]
+        if labels is not None:
+            out = (_cls_loss(self, logits, labels, soft_label),) + out
+        return out
+
+
+class BiImageBertForSequenceClassificationPlus(_FreezeMixin, BertPreTrainedModel):
+    """vl:1975-2070 — the `--use_single` variant of the VE / VQA fine-tuning scripts (run_ve.py:920-921, run_vqa.py:1208-1209):
+    the un-normalised CLIP-style global embeddings of the uni-modal stacks go through `single_mapping` and are classified
+    together with the pooled joint output.  On the product path (f32 parameters on a HIP device) the whole head is fuse_head:
+    two concat-and-dropout launches (engine.FuseFeaturesFn) around the f32 MFMA GEMMs with fused bias / ReLU; the nn.ReLU and
+    nn.Dropout modules only hold the reference's state_dict layout and serve the CPU / model.half() composition."""
+
+    def __init__(self, config):
+        super().__init__(config)
+        self.num_labels = config.num_labels
+        self.loss_type = config.loss_type
+        self.config = config
+        if config.img_feature_dim <= 0:
+            raise NotImplementedError("text-only BertModel is outside the accelerated path")
+        self.bert = BiBertImgModel(config)
+        self.dropout = nn.Dropout(config.hidden_dropout_prob)
+        H = config.hidden_size
+        self.single_mapping = nn.Sequential(HeadLinear(4 * H, 2 * H), nn.ReLU(), HeadLinear(2 * H, H))
+        self.classifier = None
+        if hasattr(config, "classifier"):
+            if not hasattr(config, "cls_hidden_scale"):
+                config.cls_hidden_scale = 2
+            if config.classifier == "linear":
+                self.classifier = HeadLinear(2 * H, config.num_labels)
+            elif config.classifier == "mlp":
+                self.classifier = nn.Sequential(HeadLinear(2 * H, H * config.cls_hidden_scale), nn.ReLU(),
+                                                HeadLinear(H * config.cls_hidden_scale, config.num_labels))
+        else:
+            self.classifier = HeadLinear(H, config.num_labels)      # vl:2009: as the reference builds it (too narrow for forward)
+        self.apply(self.init_weights)
+
+    def reinit_cls_head(self):
+        self.classifier.apply(self.init_weights)
+
+    @staticmethod
+    def _mlp(seq, x, fused):
+        """Linear - ReLU - Linear (`seq`) or one Linear on f32 rows x; fused: through the f32 MFMA GEMM with the ReLU in its epilogue."""
+        layers = list(seq) if isinstance(seq, nn.Sequential) else [seq]
+        for i, lin in enumerate(layers):
+            if not isinstance(lin, HeadLinear):
+                continue                      # the nn.ReLU holders: applied with the Linear in front of them
+            relu = i + 1 < len(layers) and isinstance(layers[i + 1], nn.ReLU)
+            if x.shape[-1] != lin.weight.shape[1]:
+                raise RuntimeError("size mismatch: %d input columns for a Linear(%d, %d)" % (x.shape[-1], lin.weight.shape[1], lin.weight.shape[0]))
+            if fused:
+                x = engine.SmallLinearFn.apply(x, lin.weight, lin.bias, "relu" if relu else None, False)
+            else:
+                x = lin(x)
+                x = F.relu(x) if relu else x
+        return x
+
+    def _fused(self, x):
+        return x.is_cuda and self.single_mapping[0].weight.dtype == torch.float32
+
+    def single_hidden(self, global_txt, global_img):
+        """single_mapping(dropout([t, i, i - t, i * t])) (vl:2040-2041)."""
+        if self._fused(global_txt):
+            x = engine.FuseFeaturesFn.apply(global_txt.float(), global_img.float(), hip.FUSE_PAIR4, self.dropout.p, self.training)
+            return self._mlp(self.single_mapping, x, True)
+        # documented torch paths only (INTEGRATION.md §1): CPU tensors, fp16 parameters of model.half() inference
+        dt = self.single_mapping[0].weight.dtype
+        t, i = global_txt.to(dt), global_img.to(dt)
+        return self._mlp(self.single_mapping, self.dropout(torch.cat([t, i, i - t, i * t], dim=1)), False)
+
+    def fuse_head(self, pooled, global_txt, global_img):
+        """pooled joint output + the two un-normalised global embeddings -> logits (vl:2040-2045)."""
+        single = self.single_hidden(global_txt, global_img)
+        if self._fused(pooled):
+            x = engine.FuseFeaturesFn.apply(pooled.float(), single, hip.FUSE_CAT2, self.dropout.p, self.training)
+            return self._mlp(self.classifier, x, True)
+        x = self.dropout(torch.cat([pooled.to(single.dtype), single], dim=1))
+        return self._mlp(self.classifier, x, False)
+
+    def forward(self, input_ids_a, token_type_ids_a=None, attention_mask_a=None, labels=None, input_ids_b=None,
+                token_type_ids_b=None, attention_mask_b=None, max_tag_length=20, position_ids_a=None,
+                position_ids_b=None, head_mask=None, img_feats=None, soft_label=False, host_counts=None):
+        """host_counts (optional, not a reference argument): see BiImageBertForVQA.forward."""
+        raw = []
+        outputs, _, _ = self.bert(input_ids_a=input_ids_a, position_ids_a=position_ids_a, token_type_ids_a=token_type_ids_a,
+                                  attention_mask_a=attention_mask_a, head_mask=head_mask, img_feats=img_feats,
+                                  input_ids_b=input_ids_b, position_ids_b=position_ids_b, token_type_ids_b=token_type_ids_b,
+                                  attention_mask_b=attention_mask_b, max_tag_length=max_tag_length, encode_hn=False,
+                                  host_counts=host_counts, raw_globals=raw)
+        logits = self.fuse_head(outputs[1], raw[0], raw[1])
         out = (logits,) + outputs[2:]
         if labels is not None:
             out = (_cls_loss(self, logits, labels, soft_label),) + out
